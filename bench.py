@@ -7,9 +7,13 @@ forward (train-mode BatchNorm + Dropout2d) -> class-weighted CE on softmax proba
 AdamW, all in hand-written HIP (librln.so).  With N>1 (launched by torch.distributed.run, one process per
 GPU) gradients are averaged with bucketed RCCL all-reduce overlapped with backward; scaling is weak.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times exactly --steps
+steps and reports them ("value" images/s, "ms_per_step").  --full adds, after the timed steps,
+  "module_api":   the same step through SimpleTrainModule.training_step -> loss.backward() -> optimizer.step(),
   "roofline":     achieved/peak of the dominant kernel class, timed live with HIP events on the launch stream,
+  "storage_*", "exact_fp32_mfma", "inference_480x640": the other storage mode, the exact-fp32 MFMA step, eval forward,
   "cpu_baseline": the CPU oracle's training step on the host cores (a bounded batch-8 sample).
+--dump-outputs DIR writes what the last timed step produced as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import ctypes
@@ -219,6 +223,19 @@ def inference_bench(dev, build, h=480, w=640):
     return out
 
 
+def dump_outputs(out_dir, eng, step_out, with_grads):
+    """The results of the last timed step as float32 .npy files (~28 MB at FCDenseNet67): what the step returned
+    (step_out: [loss, acc, bad_labels, counts...] on the engine path, [loss] on the module path) and the arenas it updated
+    in place -- parameters after AdamW, BatchNorm running statistics and, on the engine path, the step's gradients."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"step_out": step_out, "params": eng.params, "bn_running": eng.bnrun}
+    if with_grads:
+        arrays["grads"] = eng.grads
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def spawn_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher: starts N fresh worker processes (one per device, RCCL
     rendezvous on 127.0.0.1) BEFORE this process touches the GPU, relays rank 0's JSON line and fails loudly if
@@ -283,7 +300,15 @@ def main():
     ap.add_argument("--no-inference", action="store_true", help="skip the 480x640 inference object")
     ap.add_argument("--fwd-arith", default=None, help="dense 3x3 forward arithmetic: fp32 | bf16x1..3 | f16x1..2")
     ap.add_argument("--bwd-arith", default=None, help="dense 3x3 backward arithmetic: fp32 | bf16x1..3 | f16x1..2")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the module API, the roofline profile pass, the other "
+                         "storage mode, the exact-fp32 step, inference and the CPU baseline (the --no-* options thin "
+                         "this out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs and updated arenas to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -422,20 +447,22 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     loss = float(out[0])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, out, with_grads=args.api == "engine")
 
     prof = None
     instrumented_ms = None
     module_api = None
     secondary = {}
     single = world == 1 and not args.force_dist
-    if args.api == "engine" and single and not args.no_module_api:
+    if args.full and args.api == "engine" and single and not args.no_module_api:
         dt, _ = timed(ModuleStepper(model), args.steps, 2)
         module_api = {"value": round(B * args.steps / dt, 2), "unit": "images/sec",
                       "ms_per_step": round(1000.0 * dt / args.steps, 3),
                       "path": "SimpleTrainModule.training_step -> loss.backward() -> FusedAdamW.step()"}
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         prof, instrumented_ms = profile_pass(eng, stepper, args.steps)
-    if single and not args.no_secondary and args.api == "engine" and not (args.fwd_arith or args.bwd_arith):
+    if args.full and single and not args.no_secondary and args.api == "engine" and not (args.fwd_arith or args.bwd_arith):
         # the other storage mode, same workload and region, as an object of the same line
         other = "bf16" if args.dtype == "f32" else "f32"
         model2, eng2 = build(other)
@@ -512,7 +539,7 @@ def main():
                  "alg_GBps": round(q["bytes"] / (q["ms"] * 1e-3) / 1e9, 1) if q["bytes"] and q["ms"] else None}
                 for q in sorted(timed_classes, key=lambda q: -q["ms"])]
         result.update(secondary)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline()
         sys.stdout.flush()
         os.dup2(saved_stdout_fd, 1)

@@ -1,86 +1,57 @@
-"""Drop-in boundary: after ``install_aliases()`` the reference's own scripts import unchanged.
+"""Drop-in boundary: ``install_aliases()`` makes the reference's top-level import names resolve to this repository.
 
-Executes the import blocks of the reference's train.py / test.py / makeDemoVideo.py (read from /root/reference at test
-time, nothing of them is stored here) in a fresh interpreter with ``rightLaneNetwork/`` on ``sys.path`` and stand-ins
-registered for the ABSENT third-party modules only (pytorch_lightning, cv2, albumentations, dotenv, ...).  Asserts
-that the training modules / models / MyTransform are this repository's classes while ``dataManagement.dataModules``
-and ``dataManagement.myDatasets`` are the reference's files.  Build-container only: the reference never travels."""
+Two cases, each in a fresh interpreter:
+* a user's ``dataManagement`` package is importable (the reference's tree on ``sys.path``): only its leaf
+  ``myTransforms`` is swapped, so the user's ``dataModules`` / ``myDatasets`` stay theirs and their
+  ``from .myTransforms import MyTransform`` picks up the device transform.  The test writes a stand-in tree of that shape
+  (placeholder classes, plus ``models`` / ``trainingModules`` / ``myTransforms`` modules that fail if they are ever
+  imported instead of the aliases);
+* no such package: the alias package provides ``dataManagement.myTransforms`` itself."""
 import os
 import subprocess
 import sys
 import textwrap
 
-import pytest
-
-REF = "/root/reference/rightLaneNetwork"
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
+_SHADOWED = "raise ImportError('stand-in {} imported: install_aliases() did not take')\n"
+STANDIN_TREE = {
+    "dataManagement/__init__.py": "",
+    "dataManagement/myDatasets.py": "class StandInDataset:\n    pass\n",
+    "dataManagement/dataModules.py": ("from .myDatasets import StandInDataset\nfrom .myTransforms import MyTransform\n\n\n"
+                                      "class StandInDataModule:\n    pass\n"),
+    "dataManagement/myTransforms.py": _SHADOWED.format("dataManagement.myTransforms"),
+    "models/__init__.py": _SHADOWED.format("models"),
+    "trainingModules/__init__.py": _SHADOWED.format("trainingModules"),
+}
 
 DRIVER = textwrap.dedent(r'''
-    import ast, importlib.util, sys, types
+    import sys
 
-    REF, REPO = sys.argv[1], sys.argv[2]
+    STANDIN, REPO = sys.argv[1], sys.argv[2]
     sys.path.insert(0, REPO)
-    sys.path.insert(0, REF)
-
-    def standin(name, **attrs):
-        top = name.split(".")[0]
-        if top not in STUBBED and importlib.util.find_spec(top) is not None:
-            return  # really installed: use it
-        m = types.ModuleType(name)
-        m.__dict__.update(attrs)
-        sys.modules[name] = m
-        STUBBED.add(name.split(".")[0])
-        parent, _, leaf = name.rpartition(".")
-        if parent:
-            setattr(sys.modules[parent], leaf, m)
-        return m
-
-    STUBBED = set()
-    class _Any:
-        def __init__(self, *a, **k): pass
-        def __call__(self, *a, **k): return None
-    def _fn(*a, **k): return None
-    standin("pytorch_lightning", seed_everything=_fn, Trainer=_Any, LightningDataModule=_Any)
-    standin("pytorch_lightning.callbacks", ModelCheckpoint=_Any)
-    standin("pytorch_lightning.loggers", CometLogger=_Any, WandbLogger=_Any)
-    standin("pytorch_lightning.metrics")
-    standin("pytorch_lightning.metrics.functional", accuracy=_fn, dice_score=_fn, iou=_fn, confusion_matrix=_fn)
-    standin("cv2")
-    standin("dotenv", load_dotenv=_fn)
+    sys.path.insert(0, STANDIN)
 
     import sim2real_lane_segment_amd as amd
     amd.install_aliases()
-
-    def import_block(path, last_line):
-        """exec only the import statements among the first `last_line` lines of a reference script"""
-        src = "".join(open(path).readlines()[:last_line])
-        tree = ast.parse(src)
-        tree.body = [n for n in tree.body if isinstance(n, (ast.Import, ast.ImportFrom))]
-        ns = {"__name__": "ref_script"}
-        exec(compile(tree, path, "exec"), ns)
-        return ns
-
-    tr = import_block(f"{REF}/train.py", 12)
-    te = import_block(f"{REF}/test.py", 17)
-    dm = import_block(f"{REF}/makeDemoVideo.py", 10)
-
     ours = "sim2real_lane_segment_amd."
-    for ns in (tr, te, dm):
-        assert ns["SimpleTrainModule"].__module__.startswith(ours), ns["SimpleTrainModule"].__module__
-        assert ns["MMETrainingModule"].__module__.startswith(ours)
-    assert tr["TrainingBase"].__module__.startswith(ours)
-    assert te["MyTransform"].__module__.startswith(ours) and dm["MyTransform"] is te["MyTransform"]
-    # everything of dataManagement that is not on the path stays the reference's
-    for name in ("SimulatorDataModule", "TwoDomainDM", "BaseDataModule", "TwoDomainMMEDM"):
-        assert tr[name].__module__ == "dataManagement.dataModules"
-    import dataManagement.dataModules as ref_dm, dataManagement.myDatasets as ref_ds
-    assert ref_dm.__file__.startswith(REF) and ref_ds.__file__.startswith(REF)
-    assert te["RightLaneDataset"] is ref_ds.RightLaneDataset
-    assert ref_dm.MyTransform is te["MyTransform"]          # `from .myTransforms import MyTransform` -> device transform
 
-    # models.* incl. the legacy EncDecNet resolve through the alias (comparison.py:9, EncDecNet.py __main__)
+    from trainingModules.SimpleTrain import SimpleTrainModule, RightLaneModule
+    from trainingModules.MMETrainingModule import MMETrainingModule
+    from trainingModules.TrainingBase import TrainingBase
+    from dataManagement.myTransforms import MyTransform
+    for cls in (SimpleTrainModule, MMETrainingModule, TrainingBase, MyTransform):
+        assert cls.__module__.startswith(ours), cls.__module__
+
+    # the user's dataManagement package stays theirs; its relative import of myTransforms gets the device transform
+    import dataManagement, dataManagement.dataModules as dm, dataManagement.myDatasets as ds
+    for mod in (dataManagement, dm, ds):
+        assert mod.__file__.startswith(STANDIN), mod.__file__
+    assert dm.StandInDataModule.__module__ == "dataManagement.dataModules"
+    assert dm.StandInDataset is ds.StandInDataset
+    assert dm.MyTransform is MyTransform
+
+    # models.* incl. the legacy EncDecNet resolve through the alias
     from models.EncDecNet import EncDecNet, Conv, activationTypes
     from models.FCDenseNet.tiramisu import (FCDenseNet, FCDenseNet57, FCDenseNet67, FCDenseNet103, FCDenseNet57Base,
                                             FCDenseNet57Classifier, FCDenseNet67Base, FCDenseNet67Classifier,
@@ -88,21 +59,24 @@ DRIVER = textwrap.dedent(r'''
     import models.EncDecNet, models.FCDenseNet.layers
     assert EncDecNet.__module__.startswith(ours) and FCDenseNet57.__module__.startswith(ours)
     assert models.EncDecNet.EncDecNet is EncDecNet
-    from trainingModules.SimpleTrain import RightLaneModule
-    assert RightLaneModule is tr["SimpleTrainModule"]
-    m = tr["SimpleTrainModule"](lr=1e-3, lrRatio=1000, decay=1e-4, num_cls=4)   # train.py:49
+    assert RightLaneModule is SimpleTrainModule
+    m = SimpleTrainModule(lr=1e-3, lrRatio=1000, decay=1e-4, num_cls=4)
     assert len(m.state_dict()) == 434
     print("ALIAS-OK")
 ''')
 
 
 def test_reference_scripts_import_through_aliases(tmp_path):
+    for rel, src in STANDIN_TREE.items():
+        path = tmp_path / "standin" / rel
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(src)
     script = tmp_path / "alias_driver.py"
     script.write_text(DRIVER)
     env = dict(os.environ)
     env.pop("PYTHONPATH", None)
-    r = subprocess.run([sys.executable, str(script), REF, REPO], capture_output=True, text=True, timeout=300, env=env,
-                       cwd=str(tmp_path))
+    r = subprocess.run([sys.executable, str(script), str(tmp_path / "standin"), REPO], capture_output=True, text=True,
+                       timeout=300, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout + r.stderr
     assert "ALIAS-OK" in r.stdout
 

@@ -84,7 +84,7 @@ def test_checkpoint_with_namespace_hparams_and_hostile_pickle(tmp_path):
     assert not marker.exists()
 
 
-def test_cli_flags_and_optimizers():
+def test_cli_flags_and_optimizers(golden_dir):
     parser = TrainingBase.add_model_specific_args(argparse.ArgumentParser())
     a = parser.parse_args(["-lr", "0.01", "--decay", "0.001", "--lrRatio", "50"])
     assert (a.learningRate, a.decay, a.lrRatio) == (0.01, 0.001, 50)
@@ -94,7 +94,7 @@ def test_cli_flags_and_optimizers():
     (opt,), (sched,) = m.configure_optimizers()
     assert opt.param_groups[0]["weight_decay"] == 1e-4 and opt.param_groups[0]["betas"] == (0.9, 0.999)
     assert sum(p.numel() for p in opt.param_groups[0]["params"]) == 3461220
-    z = np.load("tests/golden/misc.npz")
+    z = np.load(golden_dir + "/misc.npz")
     lrs = []
     for _ in range(51):  # CosineAnnealingLR(T_max=25, eta_min=lr/lrRatio) table from the reference configuration
         lrs.append(opt.param_groups[0]["lr"])

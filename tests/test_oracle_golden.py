@@ -77,7 +77,17 @@ def test_small_nets(name, full):
         if full:
             ref = z["grad/" + k]
             np.testing.assert_allclose(g.numpy(), ref, rtol=1e-3, atol=1e-6 + 1e-4 * np.abs(ref).max())
-            np.testing.assert_allclose(ts.st[k].numpy(), z["param1/" + k], rtol=1e-4, atol=2e-5)
+            # AdamW's first step is lr * g / (|g| + eps), eps = 1e-8.  Where both gradients are below eps and not both
+            # exactly zero (conv biases in front of a BatchNorm: exactly zero, computed as 1e-10..3e-9 rounding noise),
+            # each step is under lr / 2 and follows the noise, which changes with the summation order (thread count,
+            # CPU): 39 elements of tiny_40x56, 27 of tiny_33x47.  Measured |param1 - fixture| there: up to 3.3e-4 at one
+            # thread, 7.9e-5 at 2 and 4 threads, 0 at 8 threads (the fixture's), 2.9e-5 / 1.0e-4 on another CPU at 16
+            # threads.  Those elements must stay within lr of the fixture; every other element within 2e-5.
+            g = g.numpy()
+            noise = (np.abs(ref) < 1e-8) & (np.abs(g) < 1e-8) & ((ref != 0) | (g != 0))
+            p1, r1 = ts.st[k].numpy(), z["param1/" + k]
+            np.testing.assert_allclose(p1[~noise], r1[~noise], rtol=1e-4, atol=2e-5)
+            assert float(np.abs(p1[noise] - r1[noise]).max(initial=0.0)) < 1e-3, k
         else:
             idx = sample_idx(g.numel(), 64, 1234)
             ref = z["gradsamp/" + k]
@@ -150,7 +160,10 @@ def test_fcd67_five_training_steps_vs_reference_fixture():
         scales = O.make_drop_scales(cfg, n, seed + 10 * s + 2)
         loss, acc, grads, _ = O.train_step(ts, x, y, cfg, scales, lr=1e-3, weight_decay=1e-4)
         assert abs(float(loss) - float(z["losses"][s])) < 2e-5, (s, float(loss), float(z["losses"][s]))
-        assert abs(float(acc) - float(z["accs"][s])) < 2e-3
+        # another summation order (thread count, CPU) moves the trajectory at rounding level (losses within 3e-6) and flips
+        # the argmax of a few near-tie pixels: by step 4, 8 / 0 / 1 of 38,400 pixels at 1 / 4 / 16 threads, 2 on another
+        # CPU.  acc is in percent
+        assert abs(float(acc) - float(z["accs"][s])) <= 16 * 100.0 / (n * h * w) + 1e-4, (s, float(acc))
         if s == 0:
             num = den = 0.0
             for k, g in grads.items():

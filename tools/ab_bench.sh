@@ -7,7 +7,7 @@ cp $R/sim2real_lane_segment_amd/csrc/librln.so /tmp/librln.keep.so
 for i in $(seq 1 $N); do
   for v in A B; do
     if [ $v = A ]; then cp $A $R/sim2real_lane_segment_amd/csrc/librln.so; else cp $B $R/sim2real_lane_segment_amd/csrc/librln.so; fi
-    python3 $R/bench.py --no-cpu-baseline --no-inference --no-module-api --steps 30 --warmup 5 2>/dev/null | python3 -c "
+    python3 $R/bench.py --full --no-cpu-baseline --no-inference --no-module-api --steps 30 --warmup 5 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$v', d['ms_per_step'], d['storage_bf16']['ms_per_step'])"
   done
